@@ -1,14 +1,21 @@
 """bench.py — driver benchmark: Trico encode -> decode round trip on device-resident synthetic meshes.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N > 1: launched by torch.distributed.run)
 
 One step = one pass of the hot path over one mesh per GPU: raw arrays resident in HBM ->
 trico_write_vertices + trico_write_triangles into a device-resident .trc archive -> (N > 1: RCCL gather
 of the archives to rank 0 over xGMI) -> trico_open_archive_for_reading + trico_read_* back into HBM.
 Workload = BASELINE.json configs[1]: grid(10000,5000) = 50M float xyz vertices + 100M uint32 triangles
 (1.8e9 raw bytes) per GPU; with N GPUs every rank codes its own mesh (configs[3], seeds 0x12345678+rank),
-so scaling is weak.  Before timing, the archive is checked against the reference's sha256
-(tests/golden/hashes.json) and the decoded arrays against the input (bit-exact).
+so scaling is weak.
+
+A plain run sets up, warms up (W steps), times K steps, writes the outputs of the last one if asked and prints one JSON line:
+metric, value, unit, higher_is_better, dtype and ms_per_step (wall time of one timed step), encode / decode / gather split of it.
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step computed - vertices.npy, triangles.npy (the decoded
+arrays) and archive.npy (the archive's bytes) - as float32 / float64, a fixed seeded sample of elements where an array is large,
+so that two builds can be compared output for output (the meshes are seeded: same arguments, same inputs).
+--full adds everything below; nothing of it runs in a plain run.  Before timing, the archive is checked against the reference's
+sha256 (tests/golden/hashes.json) and the decoded arrays against the input (bit-exact); the timed steps record per-kernel spans.
 
 value = raw input bytes of all ranks / wall time of (encode + gather + decode), GB/s.
 roofline  = the float-vertex encoder (north_star's target kernel): algorithmic bytes (raw vertex bytes
@@ -205,6 +212,12 @@ def parse():
     ap.add_argument("--mesh", default="grid", choices=["grid", "walk"])
     ap.add_argument("--W", type=int, default=10000)
     ap.add_argument("--H", type=int, default=5000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "a fixed seeded sample of elements where an array is large (64 MB at most in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: golden / round-trip checks, per-kernel spans, roofline (with a live PMC pass), the "
+                         "other blocks and the CPU baseline; the options below shape what --full adds")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", default="full", help="WxH of the CPU baseline's mesh; 'full' = the GPU's own mesh")
     ap.add_argument("--concurrent", default="8,16,32,64", help="archives decoded as one batch in the decode_concurrent block ('' : skip)")
@@ -222,7 +235,10 @@ def parse():
     # trico_amd.api.  Never a measurement: the line says so.
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help=argparse.SUPPRESS)
     ap.add_argument("--api", default="trico_amd.api", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _reference_streams_parallel(L, v, t, raw, K=1, reps=3):
@@ -882,6 +898,30 @@ def _headline_last(out):
     return ordered
 
 
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs writes at most this much in all (64 MB allowed; room left for the .npy headers)
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays = [(name, flat uint8 tensor / array, element dtype)] -> out_dir/<name>.npy, the elements as float32
+    (float32, 8- and 16-bit integers) or float64 (the rest; the mesh indices written here are far below 2**53, so exact).  An array
+    larger than its share of DUMP_BYTES is written as a fixed seeded sample of its elements: sorted indices that depend on the element
+    count only, the same from run to run, so that two builds of the project can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, raw, dtype in arrays:
+        dtype = np.dtype(dtype)
+        out_dtype = np.dtype(np.float32 if (dtype.kind == "f" and dtype.itemsize == 4) or (dtype.kind == "u" and dtype.itemsize <= 2) else np.float64)
+        elems = raw.reshape(-1, dtype.itemsize)
+        keep = share // out_dtype.itemsize
+        if elems.shape[0] > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, elems.shape[0], keep))
+            elems = elems.index_select(0, torch.from_numpy(idx).to(elems.device)) if torch.is_tensor(elems) else elems[idx]
+        if torch.is_tensor(elems):
+            elems = elems.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(elems).view(dtype).reshape(-1).astype(out_dtype))
+
+
 def decode_mixed(args, api, meshgen, dev, sync, dist, rank, world, real_stdout, host_only):
     """BASELINE configs[4] as the N-GPU job: every rank decodes its own archive, kinds mixed over the ranks (rank r: grid, walk, multi,
     grid, ...): float and double components, u32 and u64 index planes.  The archive is built by the rank itself before the clock
@@ -902,15 +942,18 @@ def decode_mixed(args, api, meshgen, dev, sync, dist, rank, world, real_stdout, 
     for name, d, cnt in devs:
         assert a.write(name, d, cnt) == 1, api.last_error()
     sync()
-    sha = hashlib.sha256(a.tobytes()).hexdigest()
-    parity = "unchecked (no golden for this size)"
-    hp = os.path.join(ROOT, "tests", "golden", "hashes.json")
-    if os.path.exists(hp):
-        g = json.load(open(hp)).get("%s_%dx%d" % (kind, W, H))
-        if g is not None:
-            if g["sha256"] != sha:
-                raise SystemExit("bench.py: %s archive sha256 differs from the reference's golden on rank %d" % (kind, rank))
-            parity = "sha256 == reference golden"
+    sha = None
+    parity = "not checked (bench.py --full checks it)"
+    if args.full:
+        sha = hashlib.sha256(a.tobytes()).hexdigest()
+        parity = "unchecked (no golden for this size)"
+        hp = os.path.join(ROOT, "tests", "golden", "hashes.json")
+        if os.path.exists(hp):
+            g = json.load(open(hp)).get("%s_%dx%d" % (kind, W, H))
+            if g is not None:
+                if g["sha256"] != sha:
+                    raise SystemExit("bench.py: %s archive sha256 differs from the reference's golden on rank %d" % (kind, rank))
+                parity = "sha256 == reference golden"
     outs = [torch.empty_like(d) for _, d, _ in devs]
 
     def step():
@@ -927,7 +970,7 @@ def decode_mixed(args, api, meshgen, dev, sync, dist, rank, world, real_stdout, 
 
     for _ in range(max(1, args.warmup)):
         step()
-    if not all(bool(torch.equal(o, d)) for (_, d, _), o in zip(devs, outs)):
+    if args.full and not all(bool(torch.equal(o, d)) for (_, d, _), o in zip(devs, outs)):
         raise SystemExit("bench.py: decoded arrays differ from the input on rank %d" % rank)
     barrier()
     t0 = time.perf_counter()
@@ -940,9 +983,13 @@ def decode_mixed(args, api, meshgen, dev, sync, dist, rank, world, real_stdout, 
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
-    ranks = rank_report(dist, rank, int(os.environ.get("LOCAL_RANK", "0")), world, dev, host_only,
-                        {"kind": kind, "archive_bytes": int(a.get_size()), "archive_sha256": sha[:16], "parity": parity, "decoded_bytes": int(raw),
-                         "rank_ms_per_step": round((t1 - t0) / args.steps * 1e3, 3)})
+    ranks = None
+    if args.full:
+        ranks = rank_report(dist, rank, int(os.environ.get("LOCAL_RANK", "0")), world, dev, host_only,
+                            {"kind": kind, "archive_bytes": int(a.get_size()), "archive_sha256": sha[:16], "parity": parity, "decoded_bytes": int(raw),
+                             "rank_ms_per_step": round((t1 - t0) / args.steps * 1e3, 3)})
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, [(name, o, arr.dtype) for (name, arr, _), o in zip(streams, outs)])
     if rank == 0:
         step_s = el.item() / args.steps
         out = {"metric": "decode GB/s (output bytes), mixed archives", "value": round(tot.item() / step_s / 1e9, 4), "unit": "GB/s",
@@ -953,7 +1000,9 @@ def decode_mixed(args, api, meshgen, dev, sync, dist, rank, world, real_stdout, 
                                       "triangles / double vertices + double normals + float uv + u64 triangles - built on the GPU, decoded into HBM" % (W, H),
                           "mode": "decode-mixed", "kind_rank0": kind, "decoded_bytes_all_ranks": int(tot.item()), "parity_rank0": parity,
                           "parallelism": "1 process per GPU, %d independent archives, no collective in the timed region" % world},
-               "decode_GBps": round(tot.item() / step_s / 1e9, 4), "ranks": ranks}
+               "decode_GBps": round(tot.item() / step_s / 1e9, 4)}
+        if ranks is not None:
+            out["ranks"] = ranks
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(_headline_last(out)) + "\n").encode())
     a.close()
@@ -1033,9 +1082,9 @@ def main():
         comm = CComm(api, rank, world, share)
     unit_encoder = (getattr(api, "unit_encoder", None) or hip_unit_encoder)(api) if sharded else None
 
-    def step_sharded(check=False):
+    def step_sharded(check=False, keep=False):
         """ONE mesh: every rank encodes its share of the 7 units (x, y, z, b1..b4), one exchange, rank 0 frames the archive and
-        decodes it."""
+        decodes it.  keep: the archive stays open in state["archive"] (--dump-outputs, last timed step)."""
         te0 = time.perf_counter()
         a = sharded_write(dist, api, [("vertices", d_v, nv), ("triangles", d_t, nt)], unit_encoder, root=0, device_archive=True,
                           gather=(lambda t: comm.gather(t, 0)) if comm is not None else None)
@@ -1061,14 +1110,17 @@ def main():
                     pos += 4 + nb
                 state["vertex_payload_bytes"] = vp
             r.close()
-            a.close()
+            if keep:
+                state["archive"] = a
+            else:
+                a.close()
         elif check:
             state.update(archive_bytes=0, sha256=None, roundtrip_ok=True, vertex_payload_bytes=0)
         return te1 - te0, 0.0, td1 - te1
 
-    def step(check=False):
+    def step(check=False, keep=False):
         if sharded:
-            return step_sharded(check)
+            return step_sharded(check, keep)
         te0 = time.perf_counter()
         a = api.Archive.open_for_writing(raw_bytes // 2, device=True)      # caller-chosen initial size: no regrowth, and room for the vertex stream's worst case (the writer then frames it in place)
         assert a.write("vertices", d_v, nv) == 1, api.last_error()
@@ -1102,33 +1154,37 @@ def main():
                 pos += 4 + nb
             state["vertex_payload_bytes"] = vp
         r.close()
-        a.close()
+        if keep:
+            state["archive"] = a
+        else:
+            a.close()
         return te1 - te0, tg1 - te1, td1 - tg1
 
-    # correctness gate + warmup (untimed)
-    step(check=True)
+    # warmup (untimed); with --full its first step is the correctness gate
+    step(check=args.full)
     for _ in range(max(0, args.warmup - 1)):
         step()
     golden = None
     hp = os.path.join(ROOT, "tests", "golden", "hashes.json")
-    if os.path.exists(hp):
+    if args.full and os.path.exists(hp):
         key = "%s_%dx%d" % (args.mesh, W, H) + ("" if (rank == 0 or sharded) else "_seed%08x" % seed)
         golden = json.load(open(hp)).get(key)
-    parity = "unchecked (no golden for this size)"
+    parity = "unchecked (no golden for this size)" if args.full else "not checked (bench.py --full checks it)"
     if golden is not None and state["sha256"] is not None:
         if golden["sha256"] != state["sha256"]:
             raise SystemExit("bench.py: archive sha256 differs from the reference's golden on rank %d" % rank)
         parity = "sha256 == reference golden"
-    if not state["roundtrip_ok"]:
+    if args.full and not state["roundtrip_ok"]:
         raise SystemExit("bench.py: decoded arrays differ from the input on rank %d" % rank)
 
-    L.trico_hip_profile_enable(1)
-    L.trico_hip_profile_reset()
+    if args.full:
+        L.trico_hip_profile_enable(1)
+        L.trico_hip_profile_reset()
     barrier()
     t0 = time.perf_counter()
     enc = gat = dec = 0.0
-    for _ in range(args.steps):
-        e, g, d = step()
+    for i in range(args.steps):
+        e, g, d = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
         enc += e
         gat += g
         dec += d
@@ -1139,7 +1195,7 @@ def main():
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = elapsed.tolist()
     ranks = None
-    if world > 1 or dist is not None:
+    if args.full and (world > 1 or dist is not None):
         ranks = rank_report(dist, rank, local_rank, world, dev, host_only,
                             {"mesh_seed": "%08x" % seed, "archive_bytes": int(state.get("archive_bytes") or 0), "archive_sha256": (state.get("sha256") or "")[:16],
                              "parity": ("sha256 == reference golden" if (golden is not None and state["sha256"] is not None) else "unchecked (no golden / not the framing rank)"),
@@ -1147,37 +1203,26 @@ def main():
                              "rank_ms_per_step": round((t1 - t0) / args.steps * 1e3, 3), "rank_encode_ms": round(enc / args.steps * 1e3, 3),
                              "rank_gather_ms": round(gat / args.steps * 1e3, 3), "rank_decode_ms": round(dec / args.steps * 1e3, 3)})
 
-    spans = ctypes.c_uint64(0)
     kms = {}
-    for name, kid in api.KERNEL_IDS.items():
-        ms = L.trico_hip_profile_ms(kid, ctypes.byref(spans))
-        if spans.value:
-            kms[name] = {"avg_ms": round(ms / spans.value, 4), "launches": int(spans.value)}
-    L.trico_hip_profile_enable(0)
+    if args.full:
+        spans = ctypes.c_uint64(0)
+        for name, kid in api.KERNEL_IDS.items():
+            ms = L.trico_hip_profile_ms(kid, ctypes.byref(spans))
+            if spans.value:
+                kms[name] = {"avg_ms": round(ms / spans.value, 4), "launches": int(spans.value)}
+        L.trico_hip_profile_enable(0)
+
+    if "archive" in state:
+        # what a caller of the step receives: the archive the encoder wrote and the arrays decoded from it (rank 0's)
+        last = state.pop("archive")
+        if rank == 0:
+            dump_outputs(args.dump_outputs, [("vertices", d_v2.view(torch.uint8), np.float32), ("triangles", d_t2.view(torch.uint8), np.uint32),
+                                             ("archive", np.frombuffer(last.tobytes(), np.uint8), np.uint8)])
+        last.close()
 
     if rank == 0:
         total_raw = raw_bytes * (1 if sharded else world)
         step_s = elapsed[0] / args.steps
-        fe = kms.get("fpc32_encode", {"avg_ms": float("nan")})
-        alg_bytes = v.nbytes + state["vertex_payload_bytes"]
-        achieved = alg_bytes / (fe["avg_ms"] * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(args.mesh, live=(world == 1 and not args.quick))
-        # every other stage of the step against the same peak: algorithmic bytes / live hipEvent span
-        tri_raw = t.nbytes
-        tri_pay = state["archive_bytes"] - 8 - 2 * 5 - 7 * 4 - state["vertex_payload_bytes"]
-        stage_bytes = {"planes_split": 2 * tri_raw, "lz4_encode": tri_raw + tri_pay, "lz4_decode": tri_raw + tri_pay, "planes_merge": 2 * tri_raw,
-                       "fpc32_decode": v.nbytes + state["vertex_payload_bytes"]}
-        stage_bound = {"planes_split": "hbm", "planes_merge": "hbm",
-                       "lz4_encode": "latency of the greedy parse chain per plane, made parallel by chunk speculation (DESIGN.md 4.3)",
-                       "lz4_decode": "hbm traffic of the pointer-jumping rounds, 12 B per output byte and round (DESIGN.md 4.4)",
-                       "fpc32_decode": "one dependent chain per component: see decode_model"}
-        roofline_all = []
-        for name in ("planes_split", "lz4_encode", "fpc32_decode", "lz4_decode", "planes_merge"):
-            if name in kms and sharded is False:
-                ms = kms[name]["avg_ms"]
-                gb = stage_bytes[name] / (ms * 1e-3) / 1e9
-                roofline_all.append({"stage": name, "algorithmic_bytes": stage_bytes[name], "avg_ms": ms, "achieved": round(gb, 2), "unit": "GB/s",
-                                     "peak": HBM_PEAK_GBPS, "frac": round(gb / HBM_PEAK_GBPS, 5), "bound": stage_bound[name]})
         out = {
             "metric": "encode+decode GB/s (input bytes)",
             "value": round(total_raw / step_s / 1e9, 4),
@@ -1189,7 +1234,7 @@ def main():
             "config": {"workload": "%s(%d,%d): %d float xyz vertices + %d uint32 triangles per GPU (BASELINE configs[1]%s), "
                                    "device-resident raw arrays -> .trc archive in HBM -> decoded arrays in HBM"
                                    % (args.mesh, W, H, nv, nt, "" if world == 1 else "; one mesh per GPU, RCCL gather of archives to rank 0 (configs[3])"),
-                       "raw_bytes_per_gpu": raw_bytes, "archive_bytes_rank0": state["archive_bytes"], "parity": parity,
+                       "raw_bytes_per_gpu": raw_bytes, "archive_bytes_rank0": state.get("archive_bytes"), "parity": parity,
                        "parallelism": ("1 process per GPU, ONE mesh: 7 stream units (x, y, z, b1..b4) round-robin over %d ranks, payload gather, "
                                        "archive assembled and decoded on rank 0" % world) if sharded
                                       else "1 process per GPU, %d independent meshes" % world,
@@ -1197,19 +1242,40 @@ def main():
             "encode_GBps": round(total_raw / (elapsed[1] / args.steps) / 1e9, 4),
             "decode_GBps": round(total_raw / (elapsed[3] / args.steps) / 1e9, 4),
             "gather_ms": round(elapsed[2] / args.steps * 1e3, 3),
-            "roofline": {"kernel": "float-vertex encoder (every kernel of its launch sequence, AoS vertices -> payload bytes in the archive)",
-                         "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": fe["avg_ms"],
-                         "code_sweep": {0: "two sweeps, ballots", 2: "two sweeps, lane-ordered LDS exchange", 3: "one sweep, lane-ordered LDS exchange"}.get(
-                             L.trico_hip_fpc32_code_sweep(), "?")},
-            "roofline_all": roofline_all,
-            "kernels": kms,
         }
+        if args.full:
+            fe = kms.get("fpc32_encode", {"avg_ms": float("nan")})
+            alg_bytes = v.nbytes + state["vertex_payload_bytes"]
+            achieved = alg_bytes / (fe["avg_ms"] * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(args.mesh, live=(world == 1 and not args.quick))
+            # every other stage of the step against the same peak: algorithmic bytes / live hipEvent span
+            tri_raw = t.nbytes
+            tri_pay = state["archive_bytes"] - 8 - 2 * 5 - 7 * 4 - state["vertex_payload_bytes"]
+            stage_bytes = {"planes_split": 2 * tri_raw, "lz4_encode": tri_raw + tri_pay, "lz4_decode": tri_raw + tri_pay, "planes_merge": 2 * tri_raw,
+                           "fpc32_decode": v.nbytes + state["vertex_payload_bytes"]}
+            stage_bound = {"planes_split": "hbm", "planes_merge": "hbm",
+                           "lz4_encode": "latency of the greedy parse chain per plane, made parallel by chunk speculation (DESIGN.md 4.3)",
+                           "lz4_decode": "hbm traffic of the pointer-jumping rounds, 12 B per output byte and round (DESIGN.md 4.4)",
+                           "fpc32_decode": "one dependent chain per component: see decode_model"}
+            roofline_all = []
+            for name in ("planes_split", "lz4_encode", "fpc32_decode", "lz4_decode", "planes_merge"):
+                if name in kms and sharded is False:
+                    ms = kms[name]["avg_ms"]
+                    gb = stage_bytes[name] / (ms * 1e-3) / 1e9
+                    roofline_all.append({"stage": name, "algorithmic_bytes": stage_bytes[name], "avg_ms": ms, "achieved": round(gb, 2), "unit": "GB/s",
+                                         "peak": HBM_PEAK_GBPS, "frac": round(gb / HBM_PEAK_GBPS, 5), "bound": stage_bound[name]})
+            out["roofline"] = {"kernel": "float-vertex encoder (every kernel of its launch sequence, AoS vertices -> payload bytes in the archive)",
+                               "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": fe["avg_ms"],
+                               "code_sweep": {0: "two sweeps, ballots", 2: "two sweeps, lane-ordered LDS exchange", 3: "one sweep, lane-ordered LDS exchange"}.get(
+                                   L.trico_hip_fpc32_code_sweep(), "?")}
+            out["roofline_all"] = roofline_all
+            out["kernels"] = kms
         if ranks is not None:
             out["ranks"] = ranks
         Ks = [int(k) for k in args.concurrent.split(",") if k.strip()]
-        if world == 1 and not args.no_extras and not args.quick:
+        if args.full and world == 1 and not args.no_extras and not args.quick:
             out["decode_model"] = decode_model(api, d_v, d_t, nv, nt, raw_bytes)
             out.update(extras(args, api, meshgen, dev, d_v, d_t, nv, nt, raw_bytes))
             if args.mesh == "grid":
@@ -1219,7 +1285,7 @@ def main():
                                                with_cpu=not args.no_cpu_baseline)
                 out["config5_mixed"] = out["config3"].pop("config5_mixed")
                 out["encoder_variants"] = encoder_variants(W, H)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             allK = tuple(k for k in Ks if k in (8, 16, 32)) if not (args.no_extras or args.quick) else ()
             if args.cpu_sample == "full":
                 out["cpu_baseline"] = cpu_baseline(args.mesh, W, H, v, t, allK)

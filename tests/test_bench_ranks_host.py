@@ -13,13 +13,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(shard, mode="roundtrip", ranks=2, W=1000, H=1000):
+def _run(shard, mode="roundtrip", ranks=2, W=1000, H=1000, extra=("--full",)):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1", "--warmup", "1",
            "--W", str(W), "--H", str(H), "--shard", shard, "--mode", mode, "--backend", "gloo", "--api", "tests.fake_hip_api", "--no-cpu-baseline"]
+    cmd += list(extra)
     env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), OMP_NUM_THREADS="1")
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -71,6 +72,37 @@ def test_decode_mixed_rank_body(ranks, native_libs):
     assert rk["collective"]["world_size_as_reported"] == ranks and [r["rank"] for r in rk["per_rank"]] == list(range(ranks))
     assert [r["kind"] for r in rk["per_rank"]] == ["grid", "walk", "multi"][:ranks]
     assert all(r["parity"] == "sha256 == reference golden" for r in rk["per_rank"])
+
+
+@pytest.mark.parametrize("mode", ["roundtrip", "decode-mixed"])
+def test_plain_line_and_dumped_outputs(mode, native_libs, tmp_path):
+    """A plain run (no --full) prints the headline keys only, and --dump-outputs writes what the last timed step computed: float32 /
+    float64 .npy files, 64 MB at most, the same from run to run; the decoded arrays are the input mesh."""
+    import numpy as np
+    from oracle import oracle as O
+    from trico_amd import meshgen
+    W, H = 300, 200
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        j = _run("meshes", mode=mode, ranks=1, W=W, H=H, extra=("--dump-outputs", str(d)))
+        assert j["steps"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "GB/s" and j["higher_is_better"] is True
+        assert not {"kernels", "roofline", "roofline_all", "cpu_baseline", "ranks", "other_mesh", "config3"} & set(j), sorted(j)
+        files = sorted(os.listdir(str(d)))
+        assert sum(os.path.getsize(str(d / f)) for f in files) <= 64 * 10 ** 6
+        arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1]) and all(dumps[0][k].tobytes() == dumps[1][k].tobytes() for k in dumps[0])
+    got = dumps[0]
+    v, t = meshgen.grid(W, H)
+    assert got["vertices"].tobytes() == v.tobytes() and got["triangles"].tobytes() == t.astype(np.float64).tobytes()
+    if mode == "roundtrip":
+        a = O.OracleArchive()
+        a.write("vertices", v, W * H)
+        a.write("triangles", t, 2 * W * H)
+        assert got["archive"].tobytes() == np.frombuffer(a.tobytes(), np.uint8).astype(np.float32).tobytes()
+        a.close()
 
 
 def test_committed_pmc_summary_parses():

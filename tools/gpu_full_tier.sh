@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1 || { tail -60 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
-timeout -k 10 900 python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python - <<'PY'
 import json,os
 j=json.loads(open(os.environ['GRAFT_REPO_ROOT']+'/gpurun_out/full_tier/bench.json').read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 # Collects the profiles committed under profiles/ (layout of rounds 3 and 4).  usage (GPU box): bash tools/profile_round.sh <tag>
-#   <tag>_bench_config2.json / _kernel_stats.txt      bench.py --quick under rocprofv3 --kernel-trace --stats
-#   <tag>_bench_config2_unprofiled.json               the full bench.py line, no profiler attached
+#   <tag>_bench_config2.json / _kernel_stats.txt      bench.py --full --quick under rocprofv3 --kernel-trace --stats
+#   <tag>_bench_config2_unprofiled.json               the bench.py --full line, no profiler attached
 #   <tag>_fpc32_encode_kernel_stats.txt               the float-vertex encoder ALONE (tools/perf_fpc32.py grid): per-kernel durations
 #   <tag>_fpc32_encode_hbm_traffic_pmc.txt            --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes, same program
 #   <tag>_fpc32_encode_sq_counters.txt                SQ instruction / cycle / LDS counters, same program, both meshes
@@ -14,9 +14,9 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 echo "== full bench, no profiler"
-timeout -k 10 600 python $R/bench.py --steps 3 --warmup 1 > $O/${TAG}_bench_config2_unprofiled.json 2> $O/bench_unprofiled.err
-echo "== kernel trace of bench.py --quick"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --quick --steps 3 --warmup 1 > $O/${TAG}_bench_config2.json 2> $O/bench.err
+timeout -k 10 600 python $R/bench.py --full --steps 3 --warmup 1 > $O/${TAG}_bench_config2_unprofiled.json 2> $O/bench_unprofiled.err
+echo "== kernel trace of bench.py --full --quick"
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -- python $R/bench.py --full --quick --steps 3 --warmup 1 > $O/${TAG}_bench_config2.json 2> $O/bench.err
 python $R/tools/prof_summary.py $O/bench > $O/${TAG}_bench_config2_kernel_stats.txt
 echo "== encoder alone: kernel trace, both meshes"
 { for m in grid walk; do
